@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — rays/s of the TinyNeRF train step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds per timed step) with the run's configuration.  --dump-outputs DIR then
+also writes what the last timed step returned on rank 0 — loss.npy, comp_rgb.npy (this rank's rays) and params.npy (the flat
+fp32 parameters after its Adam update) — all float32; the inputs are seeded, so two runs with the same arguments see the same data.
+Everything else below (roofline, per-kernel times, PSNR, the other pipes, precisions, shapes and the CPU baseline) runs only
+with --full.
 
 Started from a plain shell with --gpus N > 1, the parent process (before any GPU call) spawns N fresh rank processes
 of itself (tnerf/launch.py: RANK/LOCAL_RANK/WORLD_SIZE, MASTER_ADDR=127.0.0.1, a free MASTER_PORT) and relays rank 0's
@@ -16,7 +23,7 @@ Workload (BASELINE.json configs[1]): 100x100 scene, 106 views, L=6 (39 inputs), 
 synthetic scene (the dataset blob is not available offline), resident in HBM before the timed region.  N>1: one
 process per GPU, rays sharded over ranks, one all-reduce(SUM) of the 1.93 MB flat gradient per step.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  With --full, besides the contract fields it carries
   roofline     — the dominant chain kernel's algorithmic fp32 FLOP/s against the ceiling of the pipe it runs on (x3: the dense
                  fp16 MFMA peak / 3, three partial products per fp32 product), kernel time measured live with HIP events on the
                  launch stream,
@@ -166,7 +173,20 @@ def parse_args(argv=None):
     ap.add_argument("--ray-tables", action="store_true",
                     help="gather rays/targets from precomputed (N,HW,3) tables like the reference loop (train.py:94-112) "
                          "instead of generating them in the kernel from pose + pixel index")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (loss, comp_rgb, params) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every context section (roofline, per-kernel times, PSNR, fp32-MFMA pipe, bf16, other shapes, "
+                         "scaling, CPU baseline); a plain run times the headline step only")
     return ap.parse_args(argv)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor of `arrays` as out_dir/<name>.npy in float32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def main():
@@ -251,7 +271,7 @@ def run(args):
 
     import rays as rays_mod
     all_o = all_d = None
-    if args.ray_tables or rank == 0:
+    if args.ray_tables or (args.full and rank == 0):
         all_o, all_d = [], []
         for i in range(N if args.ray_tables else 1):           # train.py:94-101 (rank 0 needs image 0 for the kernel timings)
             ro, rd = rays_mod.get_rays(H, W, focal, poses[i])
@@ -289,7 +309,7 @@ def run(args):
         fence()
         t0 = time.perf_counter()
         for _ in range(n_steps):
-            one_step()
+            state["last"] = one_step()
         fence()
         dt = time.perf_counter() - t0
         if use_dist:
@@ -309,6 +329,9 @@ def run(args):
     dt = timed(args.warmup, args.steps)
     ms_per_step = dt / args.steps * 1e3
     value = R_global * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        loss_last, comp_last = state["last"]
+        dump_outputs(args.dump_outputs, {"loss": loss_last.reshape(-1), "comp_rgb": comp_last, "params": model.hip_state().flat})
 
     out = {"metric": "rays/s (train step)", "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling,
@@ -332,7 +355,7 @@ def run(args):
                       "parallelism": f"rays sharded x{world} ({args.scaling}), 1 all-reduce of {opt._st.n_params * 4} B per step" if world > 1 else "single GPU"}}
 
     # ---- the exchange step on its own: group size after a real all-reduce, and what the all-reduce costs per step
-    if use_dist:
+    if use_dist and args.full:
         g = model.hip_state().grad
         probe = torch.ones(1, device=dev)
         dist.all_reduce(probe)
@@ -346,7 +369,7 @@ def run(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         out["allreduce"] = {"bytes": int(g.numel() * 4), "us_per_step": float(t.item()) * 1e3, "ranks": dist.get_world_size(),
                             "how": "50 back-to-back all-reduces of the flat gradient between HIP events, max over ranks"}
-    else:
+    elif not use_dist:
         out["rccl_ranks"] = 1
 
     def kernel_section(st, R, S, precision):
@@ -407,7 +430,7 @@ def run(args):
         seq = {k: float(np.mean([row[i].elapsed_time(row[i + 1]) for row in marks])) for i, k in enumerate(order)}
         return {name: seq.get(name, ms) for name, ms in iso.items()}, iso
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- per-kernel times, live, HIP events on the launch stream (torch's current stream)
         model._ensure_packed()
         kern, kern_iso = kernel_section(model.hip_state(), RAYS, SAMPLES, "fp32")
@@ -455,8 +478,9 @@ def run(args):
             out["step_mfma_frac"] = step_flops / (ms_per_step * 1e-3) / 1e12 / peak
             out["step_minus_big3_us"] = (ms_per_step - sum(kern[k] for k in step_kernels)) * 1e3
 
-    held = make_synthetic_scene(n_images=8, seed=1)               # eight cameras on the same scene that are not in the training set
-    h_images = torch.from_numpy(held["images"]).to(dev); h_poses = torch.from_numpy(held["poses"]).to(dev)
+    if args.full:
+        held = make_synthetic_scene(n_images=8, seed=1)           # eight cameras on the same scene that are not in the training set
+        h_images = torch.from_numpy(held["images"]).to(dev); h_poses = torch.from_numpy(held["poses"]).to(dev)
 
     def psnr_block(mdl, extra=None):
         """Keep training (untimed), then minibatch PSNR, the full-image PSNR of one training view, and — the statistic the bf16
@@ -486,7 +510,7 @@ def run(args):
                 "heldout_checkpoint_every_steps": every}, img
 
     # ---- PSNR context
-    if args.psnr_steps > 0:
+    if args.full and args.psnr_steps > 0:
         r = psnr_block(model)
         if r:
             out["psnr"] = r[0]; img_f32 = r[1]
@@ -499,7 +523,7 @@ def run(args):
                                        "note": "same trainer, same W + K protocol as `value`, on the trained weights: the step's time depends on the data"}
 
     # ---- the same step on the plain fp32-MFMA kernels (TNERF_FLAG_FP32_MFMA): what the x3 pipe buys, driver-timed like `value`
-    if not args.no_extra and FP32_PATH_PEAK == PEAK_X3_TFLOPS:
+    if args.full and not args.no_extra and FP32_PATH_PEAK == PEAK_X3_TFLOPS:
         m32, o32, t32 = make_trainer("fp32", matrix_pipe="fp32_mfma")
         run_["tr"] = t32
         gen.manual_seed(1234); state["step"] = 0
@@ -520,7 +544,7 @@ def run(args):
     # `value` above is the contract number (weak unless --scaling strong).  Here: the same step with the global batch fixed at 4096 rays
     # (strong) resp. 4096 per rank (weak), and both again WITHOUT the all-reduce — the difference is the exposed (non-overlapped) part of
     # the exchange; allreduce.us_per_step above is the collective on its own.
-    if world > 1 and not args.no_extra and not args.parity_rng:
+    if args.full and world > 1 and not args.no_extra and not args.parity_rng:
         def other_mode():
             res = {}
             for mode in ("weak", "strong"):
@@ -552,7 +576,7 @@ def run(args):
 
     # ---- strong-scaling loads on one GPU: the step at 2048 / 1024 / 512 rays (what each of N = 2 / 4 / 8 ranks runs when 4096 rays are
     # sharded) + the cost of an RCCL all-reduce of the flat gradient in a one-rank group -> the efficiency these predict
-    if not args.no_extra and world == 1 and rank == 0:
+    if args.full and not args.no_extra and world == 1 and rank == 0:
         def small_batch():
             own_group = False
             if not dist.is_initialized():
@@ -602,7 +626,7 @@ def run(args):
             run_.update(tr=tr, R_global=R_global, lo=lo, hi=hi)
 
     # ---- bf16 mode (BASELINE.json configs[3]): same initial weights, same pixel / jitter stream, same step counts
-    if not args.no_bf16:
+    if args.full and not args.no_bf16:
         model16, opt16, tr16 = make_trainer("bf16")
         run_["tr"] = tr16
         gen.manual_seed(1234); state["step"] = 0
@@ -655,7 +679,7 @@ def run(args):
         del model16, opt16, tr16
 
     # ---- the other shapes of BASELINE.json / the reference, driver-visible (context; every rank takes part when N > 1)
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         def section(fn):
             try:
                 return fn()
@@ -740,7 +764,7 @@ def run(args):
                                "bf16": render_shape(m5, encoder, 800, 800, 4 * 138.88887889922103 * 2, ps, 256, "bf16")}}
         out["cfg5"] = section(cfg5)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scene)
     fence()
     if use_dist:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """MFMA utilisation and effective clock per kernel from a rocprofv3 PMC pass (MI355X_MICROARCH.md: SQ_VALU_MFMA_BUSY_CYCLES counts
 cycles summed over the SIMDs = 32 x N_mfma for v_mfma_f32_32x32x16_bf16; GRBM_GUI_ACTIVE is summed over the 8 XCDs):
-    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/pmc_mfma -- python3 bench.py --steps 5 --warmup 3 --psnr-steps 0 --no-cpu-baseline --no-extra
-    python3 tools/pmc_mfma_summary.py gpurun_out/pmc_mfma > profiles/r02_pmc_mfma_busy.csv"""
+    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d OUT/pmc_mfma -- python3 bench.py --full --steps 5 --warmup 3 --psnr-steps 0 --no-cpu-baseline --no-extra
+    python3 tools/pmc_mfma_summary.py OUT/pmc_mfma > profiles/r02_pmc_mfma_busy.csv"""
 import csv, glob, os, sys
 from collections import defaultdict
 root = sys.argv[1]

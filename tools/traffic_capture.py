@@ -5,9 +5,9 @@ WRITE_SIZE in SEPARATE passes; on gfx950 FETCH_SIZE tallies 128-B requests at 64
 
 On the GPU box (the profiler's program goes straight after `--`):
     cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 5 --warmup 3 --psnr-steps 0 --no-cpu-baseline --no-extra
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 5 --warmup 3 --psnr-steps 0 --no-cpu-baseline --no-extra
-    python3 tools/traffic_capture.py gpurun_out/pmc_fetch gpurun_out/pmc_write
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -- python3 bench.py --full --steps 5 --warmup 3 --psnr-steps 0 --no-cpu-baseline --no-extra
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -- python3 bench.py --full --steps 5 --warmup 3 --psnr-steps 0 --no-cpu-baseline --no-extra
+    python3 tools/traffic_capture.py OUT/pmc_fetch OUT/pmc_write
 writes profiles/r04_traffic.json and profiles/r04_traffic_bf16.json tagged with the sha of csrc/ (bench.py reports them only
 while the kernel sources are the ones that were profiled)."""
 import csv
@@ -78,7 +78,7 @@ def main():
         out[fam][key] = {"kernel": prefix, "fetch_kb_raw": round(fkb, 1), "write_kb_raw": round(wkb, 1), "fetch_correction": corr,
                          "hbm_bytes": int((fkb * corr + wkb) * 1024), "dispatches": (f or w)[1],
                          "algorithmic_bytes": algo[fam].get(key)}
-    note = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 5 --warmup 3 "
+    note = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 5 --warmup 3 "
             "--psnr-steps 0 --no-cpu-baseline --no-extra; mean per dispatch.  gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE "
             "counts half the bytes of a 16-B-per-lane coalesced read stream -> x2 where fetch_correction = 2 (the weight-gradient kernels' "
             "operand streams); the 4-B-per-lane stores/loads of the chain kernels are uncalibrated (raw values kept).")
